@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """HBM bytes per scan launch from a rocprofv3 counter pass, for bench.py's `roofline.traffic`.
 
-    rocprofv3 --pmc FETCH_SIZE -d D -o run --output-format csv -- python3 bench.py ...
+    rocprofv3 --pmc FETCH_SIZE -d D -o run --output-format csv -- python3 bench.py --full ...
     rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum -d D2 ...
     python3 tools/pmc_traffic.py --fetch D/run_counter_collection.csv --rdreq D2/run_counter_collection.csv \
         --workload crc32c:1024x65536 --bytes-per-launch 67108864 --update profiles/pmc_traffic.json

@@ -2,7 +2,7 @@
 """Match bench.py's event-timed launches with rocprofv3's kernel trace of the same run (DESIGN.md §6
 "rocprof cross-check").
 
-bench.py times every roofline figure with time_launches(): a GPU-side hold (torch.cuda._sleep, the
+bench.py --full times every roofline figure with time_launches(): a GPU-side hold (torch.cuda._sleep, the
 `spin_kernel` dispatch) followed by N launches serialised on one stream, each stamped by its own
 dispatch (hipExtLaunchKernel events).  In a kernel trace of the same command each such section is
 therefore a spin_kernel dispatch followed by the section's launches on the same queue.  This script

@@ -2,8 +2,18 @@
 """Headline benchmark: GiB/s of CRC32C over device-resident buffers (BASELINE.json `metric`), on
 BASELINE.json configs[1] (C2): batches of 1024 x 64 KiB independent buffers per GPU.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`,
+the configuration and each rank's device and own rate).  --dump-outputs DIR then writes what the timed
+steps computed: DIR/checksums.npy, the last timed step's results (one per buffer), and
+DIR/checksums_by_batch.npy, those of every resident batch the timed steps ran on; float64, a 32-bit
+checksum as one exact value, a 64-bit word as (high 32 bits, low 32 bits).  With --gpus N > 1 or
+--inproc only rank 0 / device 0 writes its results.  The inputs are seeded, so the same arguments
+give the same files on every run and build.  Everything below from "Roofline" on
+(parity samples, one-batch and queued submission, roofline, read ceiling, C4, CPU baseline, pinned-host
+end-to-end, config legs) runs only with --full, after the timed steps, and is added to the same line.
 
 A step = one C2 batch (1024 x 64 KiB, its own base and its own 1024 results) checksummed on the GPU,
 inputs already resident in HBM.  Each rank scans its own batches (buffers shard across GPUs with no
@@ -71,6 +81,13 @@ def parse(argv=None):
     ap.add_argument("--alg", default="crc32c", choices=list(ALG))
     ap.add_argument("--buffers", type=int, default=1024)
     ap.add_argument("--buffer-bytes", type=int, default=65536)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg and check (parity samples, roofline, "
+                         "one-batch and queued submission, read ceiling, C4, CPU baseline, pinned-host end-to-end, "
+                         "C3 / C5 / target-shape legs; the --no-* options trim them) and report them on the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the result buffers' checksums as DIR/<name>.npy (float64); with "
+                         "--gpus N > 1 or --inproc those of rank 0 / device 0 only")
     ap.add_argument("--batches", type=int, default=8)
     ap.add_argument("--coalesce", type=int, default=32, help="queued batches per launch (1..32)")
     ap.add_argument("--branches", type=int, default=3)
@@ -900,6 +917,37 @@ class Rig:
             for bs, st in self.prepare(self.args.warmup, self.G):
                 bs.run(st)
 
+    def dump_outputs(self, outdir):
+        """--dump-outputs: the result buffer of the last timed step (what a caller of the timed path
+        receives for that batch) as <outdir>/checksums.npy, and those of every resident batch the timed
+        steps ran on, in batch order, as <outdir>/checksums_by_batch.npy.  Read back after the timed
+        steps; the warm-up ran on the same buffers with the same inputs, so the files show what the
+        path computes, not which launch wrote a buffer last.  float64: a 32-bit
+        checksum is one exact value per buffer; a 64-bit result word is a row (high 32 bits, low 32
+        bits), XXH3-128 two such rows per buffer.  A few KiB per batch."""
+        import numpy as np
+
+        steps = self.args.steps
+        if steps < 1:
+            return
+
+        words = self.count * self.per
+        # at most 2^20 result words of a batch (16 MiB): beyond that a fixed, seeded sample of them
+        keep = np.sort(np.random.default_rng(0x5EED).choice(words, 1 << 20, replace=False)) if words > 1 << 20 else None
+
+        def f64(t):
+            v = np.array(self.eng.as_unsigned(t), dtype=np.uint64)
+            v = v if keep is None else v[keep]
+            if t.dtype.itemsize == 4:
+                return v.astype(np.float64)
+            return np.stack([v >> np.uint64(32), v & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64)
+
+        os.makedirs(outdir, exist_ok=True)
+        last = f64(self.outs[(steps - 1) % self.nb])
+        np.save(os.path.join(outdir, "checksums.npy"), last)
+        nbatch = max(1, min(steps, self.nb, (40 << 20) // last.nbytes))  # both files within 64 MB
+        np.save(os.path.join(outdir, "checksums_by_batch.npy"), np.stack([f64(self.outs[b]) for b in range(nbatch)]))
+
     def parity_sample(self):
         """the first 64 buffers of the first resident batch (written by the warm-up and the timed
         region) against the engine's host path"""
@@ -984,14 +1032,20 @@ def main_inproc(args):
     el = time.perf_counter() - t0
     step_bytes = rigs[0].step_bytes
     value = n * args.steps * step_bytes / max(el, 1e-9) / 2**30
+    if args.dump_outputs:
+        with torch.cuda.device(0):
+            rigs[0].dump_outputs(args.dump_outputs)
     devs = []
     for dv, rig in enumerate(rigs):
-        with torch.cuda.device(dv):
-            nchk, ok = rig.parity_sample()
-            roof, _ = rig.roofline()
-        devs.append(dict(rig.device_record(), kernel_ms=roof["kernel_ms"], frac=roof["frac"],
-                         roofline={k: roof[k] for k in ("achieved", "frac", "kernel_ms", "bytes_per_launch")},
-                         parity_sample_buffers=nchk, parity=ok))
+        rec = rig.device_record()
+        if args.full:
+            with torch.cuda.device(dv):
+                nchk, ok = rig.parity_sample()
+                roof, _ = rig.roofline()
+            rec.update(kernel_ms=roof["kernel_ms"], frac=roof["frac"],
+                       roofline={k: roof[k] for k in ("achieved", "frac", "kernel_ms", "bytes_per_launch")},
+                       parity_sample_buffers=nchk, parity=ok)
+        devs.append(rec)
     used = distinct_devices(devs)
     gsz = widest(max(args.steps, 1), rigs[0].G)
     rec = {
@@ -1006,15 +1060,16 @@ def main_inproc(args):
                              f"({gsz} per launch) on its own HIP stream",
                    "parallelism": f"one process, {n} device(s), no collective"},
         "pct_hbm_peak": round(100.0 * value * 2**30 / 1e9 / n / HBM_PEAK_GBS, 2),
-        "per_gpu_gibs": round(value / n, 2), "devices_used": used,
-        "parity": all(d["parity"] for d in devs), "devices": devs,
-        "roofline": dict(devs[0]["roofline"], bound="hbm", peak=HBM_PEAK_GBS, unit="GB/s",
-                         kernel=kernel_name(args.alg, args.buffers, args.buffer_bytes)),
+        "per_gpu_gibs": round(value / n, 2), "devices_used": used, "devices": devs,
     }
+    if args.full:
+        rec["parity"] = all(d["parity"] for d in devs)
+        rec["roofline"] = dict(devs[0]["roofline"], bound="hbm", peak=HBM_PEAK_GBS, unit="GB/s",
+                               kernel=kernel_name(args.alg, args.buffers, args.buffer_bytes))
     print(json.dumps(rec), flush=True)
     if used != n:
         raise PlumbingError(f"--inproc --gpus {n} ran on {used} distinct device(s)")
-    if not rec["parity"]:
+    if not rec.get("parity", True):
         raise SystemExit(1)
 
 
@@ -1078,6 +1133,65 @@ def main_rank(args):
     # regions need not overlap, so there `value` is no N-GPU rate and the span is reported beside it
     span = max_over_ranks(w1) + max_over_ranks(-w0)
     value = world * args.steps * step_bytes / max(elapsed, 1e-9) / 2**30
+    if args.dump_outputs and rank == 0:
+        rig.dump_outputs(args.dump_outputs)
+
+    def headline(used, ranks):
+        """the result line of a plain run; --full adds its legs to it"""
+        return {
+            "metric": metric_name(alg),
+            "value": round(value, 2),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / max(args.steps, 1) * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic (torch.randint bytes on device)",
+            "config": {"workload": f"{config_label(alg, count, L)}: {count} x {L // 1024} KiB independent buffers per step, "
+                                   f"{alg.upper()}, device-resident, per GPU",
+                       "buffers_per_step": count, "buffer_bytes": L, "rotating_batches": nb,
+                       "resident_bytes_per_gpu": nb * step_bytes,
+                       "launch": f"aws_crt_amd_checksum_batches, up to {G} queued batches per launch "
+                                 f"({len(split(max(args.steps, 1), G)) - 1} launches for {args.steps} steps)",
+                       "streams": len(streams),
+                       "parallelism": f"buffers sharded over {world} rank(s) on {used} GPU(s), no collective"
+                                      + (" (gloo rehearsal: ranks share devices)" if shared else "")},
+            "pct_hbm_peak": round(100.0 * value * 2**30 / 1e9 / world / HBM_PEAK_GBS, 2),
+            "per_gpu_gibs": round(value / world, 2),
+            "devices_used": used,
+            "shared_devices": shared,
+            "span_ms": round(span * 1e3, 4),
+            "ranks": ranks,
+            **({"note": "gloo rehearsal on shared devices: value is not an N-GPU rate"} if shared else {}),
+        }
+
+    def finish(used, parity):
+        """RCCL ranks each need their own GPU (rank_layout refused a rank without one); a job whose
+        ranks ran on fewer distinct devices than --gpus without asking for the gloo rehearsal is not an
+        N-GPU measurement"""
+        if world > 1:
+            dist.destroy_process_group()
+        if used != world and not shared:
+            raise PlumbingError(f"{world} ranks ran on {used} distinct GPU(s)")
+        if not parity:
+            raise SystemExit(1)
+
+    if not args.full:
+        # a plain run ends here: each rank's device and own rate, gathered on rank 0, and the line
+        mine = dict({"rank": rank, "local_rank": local}, **rig.device_record())
+        mine.update({"value": round(args.steps * step_bytes / max(own, 1e-9) / 2**30, 2), "unit": "GiB/s"})
+        ranks = [mine]
+        if world > 1:
+            ranks = [None] * world
+            dist.all_gather_object(ranks, mine)
+        used = distinct_devices(ranks)
+        if rank == 0:
+            print(json.dumps(headline(used, ranks)), flush=True)
+        return finish(used, True)
 
     # the same K steps submitted one launch per batch (--coalesce 1), timed the same way: the rate a
     # caller that never queues batches together sees (reported beside `value`, never as it)
@@ -1224,36 +1338,8 @@ def main_rank(args):
                                                              coalesce=12, timing=2, do_cpu=False, do_e2e=False)
 
     if rank == 0:
-        rec = {
-            "metric": metric_name(alg),
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / max(args.steps, 1) * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (torch.randint bytes on device)",
-            "config": {"workload": f"{config_label(alg, count, L)}: {count} x {L // 1024} KiB independent buffers per step, "
-                                   f"{alg.upper()}, device-resident, per GPU",
-                       "buffers_per_step": count, "buffer_bytes": L, "rotating_batches": nb,
-                       "resident_bytes_per_gpu": nb * step_bytes,
-                       "launch": f"aws_crt_amd_checksum_batches, up to {G} queued batches per launch "
-                                 f"({len(split(max(args.steps, 1), G)) - 1} launches for {args.steps} steps)",
-                       "streams": len(streams),
-                       "parallelism": f"buffers sharded over {world} rank(s) on {used} GPU(s), no collective"
-                                      + (" (gloo rehearsal: ranks share devices)" if shared else "")},
-            "pct_hbm_peak": round(100.0 * value * 2**30 / 1e9 / world / HBM_PEAK_GBS, 2),
-            "per_gpu_gibs": round(value / world, 2),
-            "devices_used": used,
-            "shared_devices": shared,
-            "span_ms": round(span * 1e3, 4),
+        rec = dict(headline(used, ranks), **{
             "parity": parity_all,
-            "ranks": ranks,
-            **({"note": "gloo rehearsal on shared devices: value is not an N-GPU rate"} if shared else {}),
             "box": box_state(torch.cuda.get_device_properties(dev)),
             "one_batch_per_launch": one_per_launch,
             "queued_one_at_a_time": queued,
@@ -1261,17 +1347,9 @@ def main_rank(args):
             "cpu_baseline": cpu,
             "e2e_pinned": e2e,
             "configs": configs or None,
-        }
+        })
         print(json.dumps(rec), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
-    # RCCL ranks each need their own GPU (rank_layout refused a rank without one); a job whose ranks
-    # ran on fewer distinct devices than --gpus without asking for the gloo rehearsal is not an N-GPU
-    # measurement
-    if used != world and not shared:
-        raise PlumbingError(f"{world} ranks ran on {used} distinct GPU(s)")
-    if not parity_all:
-        raise SystemExit(1)
+    finish(used, parity_all)
 
 
 def main(argv=None):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of builds of the library on one box: ab/lib$v.so (v in ${VARIANTS:-A B}) are swapped into
 # aws-crt-cpp_amd/lib/ alternately and the same bench command runs against each, REPS times.
-#   REPS=3 bash scripts/ab_lib.sh python -u bench.py --steps 20 ...
+#   REPS=3 bash scripts/ab_lib.sh python -u bench.py --full --steps 20 ...   (the line's roofline is read)
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/${TAG:-ab}; mkdir -p $O

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2",
            "--cpu-seconds", "0.2", "--no-configs", "--no-c4", "--e2e-batches", "0", "--timing-launches", "4"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -46,6 +46,46 @@ def test_bench_json_line():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full: the headline line alone (no secondary leg on it), --steps timed steps, and
+    --dump-outputs writes the timed steps' checksums.  The inputs are seeded: the same seed here gives
+    the same bytes, and the oracle's CRC32C of them is what the run dumped."""
+    import numpy as np
+    import torch
+
+    from oracle import oracle
+
+    out = tmp_path / "dump"
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "GiB/s" and d["dtype"] == "u8"
+    assert d["higher_is_better"] is True and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    # value and ms_per_step describe the same 3 steps of 1024 x 64 KiB
+    assert abs(d["value"] - (64 << 20) / (d["ms_per_step"] * 1e-3) / 2**30) <= 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "e2e_pinned", "configs", "one_batch_per_launch", "queued_one_at_a_time",
+              "parity", "box"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["checksums.npy", "checksums_by_batch.npy"]
+    last, by_batch = np.load(out / "checksums.npy"), np.load(out / "checksums_by_batch.npy")
+    assert last.dtype == np.float64 and last.shape == (1024,) and by_batch.shape == (3, 1024)
+    assert np.array_equal(last, by_batch[2])  # the last of the 3 steps wrote resident batch 2
+    nb, L, k = d["config"]["rotating_batches"], 65536, 5
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0x5EED)
+    data = torch.randint(0, 256, (nb * 1024 * L,), dtype=torch.uint8, device="cuda", generator=g)
+    for b in range(3):
+        h = data[b * 1024 * L: b * 1024 * L + k * L].cpu().numpy()
+        assert [int(v) for v in by_batch[b][:k]] == [oracle.checksum("crc32c", h[i * L:(i + 1) * L]) for i in range(k)]
+
+
+@pytest.mark.gpu
 def test_bench_c4_leg_one_gpu():
     """--gpus 1: the C4 leg scans the whole 8 GiB set on the one GPU (one strided launch per pass) and
     its digest matches the golden one; C2 stays the line's value"""
@@ -64,8 +104,8 @@ def test_bench_c4_leg_one_gpu():
 
 
 def _bench(args, timeout=300, cpu=False, c4=False):
-    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-configs",
-           "--e2e-batches", "0", "--timing-launches", "4", "--no-read-ceiling"]
+    cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2",
+           "--no-configs", "--e2e-batches", "0", "--timing-launches", "4", "--no-read-ceiling"]
     cmd += ["--cpu-seconds", "0.2"] if cpu else ["--no-cpu-baseline"]
     cmd += ["--c4-passes", "1"] if c4 else ["--no-c4"]
     cmd += args

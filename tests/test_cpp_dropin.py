@@ -9,6 +9,7 @@ reference is copied into this repo.
 GPU suite: the same binaries with AWS_CRT_AMD_DISPATCH=gpu, which routes host buffers through the
 gfx950 kernels; the driver prints the fallback count, which must be 0 (every value came from the GPU).
 """
+import json
 import os
 import subprocess
 
@@ -58,19 +59,42 @@ def test_dropin_tests_run_on_gpu(engine):
     assert "dispatch 2, gpu fallbacks 0" in r.stdout, r.stdout
 
 
-@pytest.mark.gpu
-def test_reference_test_files_run_on_gpu(engine):
-    """The reference's CRCTest.cpp / XXHashTest.cpp (compiled unmodified in the build container and
-    shipped as a binary) with the host buffers routed through the gfx950 kernels: every
-    CRC32/CRC32C/CRC64NVME/XXH64/XXH3 known answer computed on the GPU, zero fallbacks."""
-    exe = os.path.join(CPP, "build", "reference_tests")
-    if not os.path.exists(exe):
-        pytest.skip("reference_tests binary not built (needs the reference checkout at build time)")
-    r = _run("reference_tests", {"AWS_CRT_AMD_DISPATCH": "gpu"})
+def _known_answers(dispatch):
+    """tests/cpp/known_answers_test.cpp on the cases of tests/golden/reference_known_answers.json (the
+    known answers of the reference's CRCTest.cpp / XXHashTest.cpp, through the same C++ surface)"""
+    cases = json.load(open(os.path.join(REPO, "tests", "golden", "reference_known_answers.json")))["cases"]
+    assert [c["name"] for c in cases] == list(REF_CASES)
+    _make("build/known_answers")
+    exe = os.path.join(CPP, "build", "known_answers")
+    args = [a for c in cases for a in (c["name"], c["alg"], c["input_hex"], c["expected_hex"])]
+    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, AWS_CRT_AMD_DISPATCH=dispatch))
     assert r.returncode == 0, r.stdout + r.stderr
     for name in REF_CASES:
         assert f"[PASS] {name}" in r.stdout, r.stdout
+    assert "6 ran, 0 failed" in r.stdout, r.stdout
+    return r
+
+
+def test_reference_known_answers_cpu():
+    _known_answers("cpu")
+
+
+@pytest.mark.gpu
+def test_reference_test_files_run_on_gpu(engine):
+    """The known answers of the reference's CRCTest.cpp / XXHashTest.cpp with the host buffers routed
+    through the gfx950 kernels: every CRC32/CRC32C/CRC64NVME/XXH64/XXH3 known answer computed on the
+    GPU, zero fallbacks.  Always from the stored cases (tests/golden/reference_known_answers.json);
+    where the reference's own files were compiled (unmodified, by the CPU test above) that binary runs
+    the same way too."""
+    r = _known_answers("gpu")
     assert "dispatch 2, gpu fallbacks 0" in r.stdout, r.stdout
+    if os.path.exists(os.path.join(CPP, "build", "reference_tests")):
+        r = _run("reference_tests", {"AWS_CRT_AMD_DISPATCH": "gpu"})
+        assert r.returncode == 0, r.stdout + r.stderr
+        for name in REF_CASES:
+            assert f"[PASS] {name}" in r.stdout, r.stdout
+        assert "dispatch 2, gpu fallbacks 0" in r.stdout, r.stdout
 
 
 def test_checksum_library_beside_another_aws_c_common():
