@@ -4,13 +4,22 @@ The framing (prelude CRC32 over 8 bytes, message CRC32 over every byte before th
 aws-c-event-stream wire format; that library is absent from the reference checkout (initialised at
 source/Api.cpp:51), so the span layout is checked here against its definition and the CRC values
 against the oracle.  Parity of the message CRC with a real event-stream encoder: unpinned.
+
+The check_frames tests compare (prelude_crc, message_crc, status) of every frame with zlib.  They
+cannot observe whether a wave ran eventstream_flat_kernel's flat path or its one-lane-per-message
+path: both give the same answer.  Which path a wave takes, and with what chunk size, join distances
+and ends per block, is predicted on the CPU from the offsets (tests/eventstream_cases.wave_classes);
+tests/test_eventstream_cases.py asserts that the streams used here cover the flat path's branches.
 """
 import random
 import struct
+import zlib
 
 import pytest
 
 from aws_crt_amd.eventstream import MIN_MESSAGE_BYTES, frame_spans
+from tests.eventstream_cases import MALFORMED, NAMED_IDS, fuzz_streams, named_stream, wave_classes
+from tests.eventstream_cases import packed as _packed
 
 
 def test_frame_spans_layout():
@@ -173,59 +182,42 @@ def test_check_frames_argument_types():
         check_frames(base, torch.zeros(4, dtype=torch.int64)[::2])
 
 
-def _packed(lens, seed, lead=0, corrupt=False):
-    """messages packed back to back after `lead` bytes (a stream of frames, eventstream_flat_kernel's
-    shape), with correct stored CRCs unless corrupted; returns blob, offsets, expected (pre, msg, st)"""
-    import zlib
-
-    rng = random.Random(seed)
-    blob = bytearray(rng.randbytes(lead))
-    offs, want = [], []
-    for i, total in enumerate(lens):
-        offs.append(len(blob))
-        m = bytearray(struct.pack(">II", total, rng.randint(0, total - 16)) + bytes(4) + rng.randbytes(total - 12))
-        pre = zlib.crc32(bytes(m[:8]))
-        m[8:12] = struct.pack(">I", pre)
-        msg = zlib.crc32(bytes(m[:total - 4]))
-        m[total - 4:] = struct.pack(">I", msg)
-        st = 3
-        if corrupt and i % 5 == 1:  # stored prelude CRC wrong
-            m[9] ^= 0x10
-            msg = zlib.crc32(bytes(m[:total - 4]))
-            m[total - 4:] = struct.pack(">I", msg)
-            st = 2
-        elif corrupt and i % 5 == 2:  # body flipped after the message CRC was stored
-            m[rng.randrange(12, total - 4) if total > 16 else 12] ^= 0x04
-            msg = zlib.crc32(bytes(m[:total - 4]))
-            st = 1
-        elif corrupt and i % 5 == 3:  # stored message CRC wrong
-            m[total - 1] ^= 0x80
-            st = 1
-        blob += m
-        want.append((pre, msg, st))
-    blob += rng.randbytes(64)
-    return blob, offs, want
-
-
-def _run_frames(blob, offs, order=None):
+def _device_bytes(blob):
     import numpy as np
+    import torch
+
+    d = torch.from_numpy(np.frombuffer(bytes(blob), dtype=np.uint8).copy()).cuda()
+    # the flat kernel's geometry depends on the base address mod 16: the CPU predictions are for this
+    assert d.data_ptr() % 16 == 0
+    return d
+
+
+def _triples(pre, msg, st):
+    u = lambda t: [int(x) & 0xFFFFFFFF for x in t.cpu().tolist()]  # noqa: E731
+    return list(zip(u(pre), u(msg), u(st)))
+
+
+def _run_frames(blob, offs, order=None, limit=None, view=0):
+    """check_frames over the frames at `offs` of `blob`; view = k: the buffer is handed over as the
+    view [k:] of an allocation with k more bytes in front"""
     import torch
 
     from aws_crt_amd.eventstream import check_frames
 
-    d = torch.from_numpy(np.frombuffer(bytes(blob), dtype=np.uint8).copy()).cuda()
+    d = _device_bytes(bytes([0xA5] * view) + bytes(blob))[view:]
     o_t = torch.tensor(offs if order is None else [offs[i] for i in order], dtype=torch.int64, device="cuda")
-    pre, msg, st = check_frames(d, o_t)
+    pre, msg, st = check_frames(d, o_t, limit=limit)
     torch.cuda.synchronize()
-    u = lambda t: [int(x) & 0xFFFFFFFF for x in t.cpu().tolist()]  # noqa: E731
-    return list(zip(u(pre), u(msg), u(st)))
+    return _triples(pre, msg, st)
 
 
 @pytest.mark.gpu
 def test_check_frames_packed(engine):
     """packed streams (the balanced flat kernel): every start alignment of the first message, random
     16..1024-byte mixes with a partial last wave, the shortest messages (several ends per 64-byte block),
-    messages spanning many chunks, corrupted CRCs, all against zlib"""
+    corrupted CRCs, all against zlib.  The last list (frames up to 70000 bytes) puts every wave over the
+    flat kernel's region bound: it checks the lane path on long frames; long frames on the flat path are
+    test_check_frames_flat_classes'."""
     rng = random.Random(0xF1A)
     for lead in (0, 1, 7, 8, 13, 31, 47, 63):
         lens = [rng.randint(16, 1024) for _ in range(64 * 6 + 5)]
@@ -258,3 +250,116 @@ def test_check_frames_packed_fallbacks(engine):
     lens[100] = 300000
     blob, offs, want = _packed(lens, 12, 9)
     assert _run_frames(blob, offs) == want
+
+
+def _flags(offs, limit, base=0):
+    return [c["flat"] for c in wave_classes(base, offs, limit)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("corrupt", [False, True], ids=["clean", "corrupt"])
+@pytest.mark.parametrize("name", NAMED_IDS)
+def test_check_frames_flat_classes(engine, name, corrupt):
+    """the named streams of tests/eventstream_cases.py (frames of 200000 and 250000 bytes joined over
+    up to 63 chunks with all four hex digits of the distance, a region of exactly the flat bound and one
+    16 bytes over it, 16- and 32-byte chunks, four end words in one block), clean and corrupted"""
+    blob, offs, want = named_stream(name, corrupt)
+    assert _run_frames(blob, offs) == want
+
+
+@pytest.mark.gpu
+def test_check_frames_flat_fuzz(engine):
+    """the seeded fuzz streams (runs of tiny, short and mid frames with up to two giants per wave, every
+    lead 0..15, about half corrupted), one call per stream"""
+    for k, (lens, lead, corrupt, seed) in enumerate(fuzz_streams()):
+        blob, offs, want = _packed(lens, seed, lead, corrupt)
+        got = _run_frames(blob, offs)
+        bad = [i for i in range(len(want)) if got[i] != want[i]]
+        assert not bad, (k, lead, corrupt, bad[:8], [lens[i] for i in bad[:8]])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 127, 128, 129, 512, 513, 577])
+def test_check_frames_counts(engine, n):
+    """frame counts around the wave (64) and workgroup (512) sizes: the last wave always runs the lane
+    path (its last frame has no next offset); with n = 65 and 513 a flat wave's last lane reads the
+    offset of a frame in the next wave / workgroup"""
+    rng = random.Random(0xC0 + n)
+    lens = [rng.randint(16, 300) for _ in range(n)]
+    blob, offs, want = _packed(lens, n, n % 16, corrupt=n % 2 == 1)
+    assert _flags(offs, len(blob)) == [True] * ((n - 1) // 64) + [False]
+    assert _run_frames(blob, offs) == want
+
+
+@pytest.mark.gpu
+def test_check_frames_limit_and_views(engine):
+    """an explicit limit (at the last frame's end; one byte short of it; inside a wave that would
+    otherwise be flat), a base that is a view at 1, 3 and 8 bytes into its allocation, and a wave whose
+    offsets look packed while a prelude says otherwise"""
+    rng = random.Random(0x11B)
+    lens = [rng.randint(16, 300) for _ in range(200)]
+    blob, offs, want = _packed(lens, 21, 6, corrupt=True)
+    end = offs[-1] + lens[-1]
+    assert _flags(offs, end) == [True, True, True, False]
+    assert _run_frames(blob, offs, limit=end) == want
+    assert _run_frames(blob, offs, limit=end - 1) == want[:-1] + [MALFORMED]
+    for cut in (offs[100] + 5, offs[100] + lens[100] - 1, offs[127] + lens[127] - 1):
+        assert _flags(offs, cut) == [True, False, False, False]  # end63 of wave 1 is past the limit
+        cut_want = [w if o + t <= cut else MALFORMED for o, t, w in zip(offs, lens, want)]
+        assert MALFORMED in cut_want[64:128] and cut_want[:64] == want[:64]
+        assert _run_frames(blob, offs, limit=cut) == cut_want, cut
+    # views: the base is not 4- or 16-aligned; with lead 4 the first frame's "4 bytes in front" start at
+    # the view's first byte, with lead 0 there are none
+    lens = [rng.randint(16, 300) for _ in range(130)]
+    for view in (1, 3, 8):
+        for lead in (4, 0):
+            blob, offs, want = _packed(lens, 30 + view, lead, corrupt=lead == 0)
+            assert _flags(offs, len(blob), base=view) == [True, True, False]
+            assert _run_frames(blob, offs, view=view) == want, (view, lead)
+    # frame 70 (200 bytes) holds a whole valid 64-byte frame at +40 that is listed as the next offset:
+    # offsets 16 or more apart, so the wave starts on the flat path, finds total_length != spacing and is
+    # redone one lane per frame, each frame judged on its own bytes
+    lens = [rng.randint(16, 300) for _ in range(130)]
+    lens[70] = 200
+    blob, offs, want = _packed(lens, 41, 2)
+    o = offs[70]
+    (inner, _, (inner_want,)) = _packed([64], 42)
+    blob[o + 40:o + 104] = inner[:64]
+    msg = zlib.crc32(bytes(blob[o:o + 196]))
+    blob[o + 196:o + 200] = struct.pack(">I", msg)
+    want[70] = (want[70][0], msg, 3)
+    offs2, want2 = offs[:71] + [o + 40] + offs[71:], want[:71] + [inner_want] + want[71:]
+    assert _flags(offs2, len(blob)) == [True, True, False]  # from the offsets alone
+    assert _run_frames(blob, offs2) == want2
+
+
+@pytest.mark.gpu
+def test_check_frames_graph_replay(engine):
+    """check_frames on a flat wave with a 200000-byte frame captured into a HIP graph (after one eager
+    call on the capture stream: the image buffer is built outside capture) replays correctly, also
+    after the buffer's bytes change"""
+    import torch
+
+    from aws_crt_amd.eventstream import check_frames
+
+    blob, offs, want = named_stream("one_long")
+    d = _device_bytes(blob)
+    o_t = torch.tensor(offs, dtype=torch.int64, device="cuda")
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        check_frames(d, o_t, stream=s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        out = check_frames(d, o_t, stream=s)
+    for it in range(3):
+        if it:
+            blob, offs2, want = named_stream("one_long", corrupt=it == 2, seed=0x6A0 + it)
+            assert offs2 == offs
+            d.copy_(_device_bytes(blob))
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s):
+            g.replay()
+        torch.cuda.synchronize()
+        assert _triples(*out) == want, it
