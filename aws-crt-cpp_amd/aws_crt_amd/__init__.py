@@ -54,6 +54,8 @@ def lib() -> ctypes.CDLL:
         L.aws_crt_amd_cpu_batch.argtypes = [ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(sz), sz,
                                             ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.c_int]
         L.aws_crt_amd_checksum_strided.argtypes = [ctypes.c_int, vp, sz, sz, sz, vp, vp, vp]
+        L.aws_crt_amd_crc32_dual_strided.argtypes = [vp, sz, sz, sz, vp, vp, vp]
+        L.aws_crt_amd_crc32_dual_fused_launches.restype = ctypes.c_ulonglong
         L.aws_crt_amd_checksum_list.argtypes = [ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(sz), sz, vp, vp, vp]
         L.aws_crt_amd_checksum_host.argtypes = [ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(sz), sz, vp, vp]
         L.aws_crt_amd_crc_combine_batch.argtypes = [ctypes.c_int, vp, vp, ctypes.POINTER(u64), sz, vp, vp]
@@ -212,6 +214,29 @@ def checksum_strided(alg: int, base, stride: int, length: int, count: int, seeds
     _check(lib().aws_crt_amd_checksum_strided(alg, addr, stride, length, count, sp, out.data_ptr(),
                                               _stream_handle(stream)))
     return out
+
+
+def checksum_dual_strided(base, stride: int, length: int, count: int, seeds=None, out=None, stream=None,
+                          base_offset: int = 0):
+    """CRC32 and CRC32C of `count` device buffers [base + i*stride + base_offset, +length) from one read
+    of the data (aws_crt_amd_crc32_dual_strided).  `seeds`: an int32 tensor of (count, 2) previous CRCs
+    or None.  Returns an int32 tensor of shape (count, 2): column 0 CRC32, column 1 CRC32C (reinterpret
+    as unsigned)."""
+    import torch
+
+    addr = (base.data_ptr() if hasattr(base, "data_ptr") else int(base)) + base_offset
+    dev = base.device if hasattr(base, "device") else torch.device("cuda")
+    if out is None:
+        out = torch.empty((count, 2), dtype=torch.int32, device=dev)
+    sp = seeds.data_ptr() if seeds is not None else None
+    _check(lib().aws_crt_amd_crc32_dual_strided(addr, stride, length, count, sp, out.data_ptr(),
+                                                _stream_handle(stream)))
+    return out
+
+
+def dual_fused_launches() -> int:
+    """Launches of the fused CRC32 + CRC32C kernel made by this process."""
+    return int(lib().aws_crt_amd_crc32_dual_fused_launches())
 
 
 def stream_release(stream) -> None:

@@ -37,16 +37,12 @@
 
 #include "engine.h"
 #include "gf2.h"
+#include "crc_device_common.h"
 
 using namespace amdcrc;
 
 namespace {
 
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) const v4u gv4u;
-typedef __attribute__((address_space(1))) const uint32_t gu32;
-typedef __attribute__((address_space(1))) const uint64_t gu64;
 
 // floor(n / d) for wave-uniform n and d >= 1.  The compiler's 64-bit integer division is ~150 scalar
 // instructions (issued at most one per 4 cycles per SIMD); the W=32 streaming scan's prologue had nine
@@ -70,13 +66,6 @@ __device__ __forceinline__ uint64_t udiv_u(uint64_t n, uint64_t d) {
     return q;
 }
 
-__device__ __forceinline__ uint32_t lds32(const char *L, uint32_t a) { return *(const uint32_t *)(L + a); }
-__device__ __forceinline__ uint64_t lds64(const char *L, uint32_t a) { return *(const uint64_t *)(L + a); }
-
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // Scalar (SMEM) loads of wave-uniform descriptor words: they retire on lgkmcnt, so waiting for them
 // never drains the vector-memory queue holding the prefetched payload groups.
@@ -95,31 +84,6 @@ __device__ __forceinline__ uint32_t sload32(const void *a) {
     return v;
 }
 
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-__device__ __forceinline__ uint32_t xor_and(uint32_t acc, uint32_t c, uint32_t m) {  // acc ^ (c & m)
-    uint32_t r;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x78" : "=v"(r) : "v"(acc), "v"(c), "v"(m));
-    return r;
-}
-
-// XOR over the 64 lanes, returned wave-uniform: two quad_perm and two row_ror DPP steps leave each
-// 16-lane row's XOR in all its lanes; four readlanes finish in scalar registers.
-__device__ __forceinline__ uint32_t wave_xor_s(uint32_t v) {
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false);  // row_ror:4
-    v ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-    return (uint32_t)(__builtin_amdgcn_readlane((int)v, 0) ^ __builtin_amdgcn_readlane((int)v, 16) ^
-                      __builtin_amdgcn_readlane((int)v, 32) ^ __builtin_amdgcn_readlane((int)v, 48));
-}
-__device__ __forceinline__ uint64_t wave_xor64_s(uint64_t v) {
-    const uint32_t lo = wave_xor_s((uint32_t)v), hi = wave_xor_s((uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // ------------------------------------------------------------------------------------------
 // Work decomposition (engine.h): buffer b = [ptr, end) is head [ptr, H) (H = ptr rounded up to 16),
@@ -548,49 +512,8 @@ struct BGroup {
 // the row is fully used, the constants region at kBKOff is unchanged).  In slot k < 4 a lane reads
 // byte q = (k + j) & 3 of lo (table 7 - q), in slot 4 + k the same byte of hi (table 3 - q), with
 // j = (lane >> 3) & 3 and copy lane & 7: a ds_read_b32 half-wave meets 32 distinct dword columns.
-constexpr uint32_t kW8Row = 512;
-constexpr int kW8RowsPerGroup = 8;  // 4 KiB per wave per ring slot, as the 4-byte rows
 static_assert(kW8Row * kW8RowsPerGroup == kBraidRow * kBraidRowsPerGroup, "ring slot size");
 
-template <uint32_t POLY>
-struct BraidW8Basis {
-    uint32_t b[9][8];  // b[t][i] = T'_t[1 << i] (t < 8); b[8][i] = T_0[1 << i]
-    constexpr BraidW8Basis() : b() {
-        const uint64_t skip = gf2_xpow8n(kW8Row - 8, POLY, 32);
-        for (int i = 0; i < 8; ++i) {
-            for (int t = 0; t < 8; ++t) b[t][i] = (uint32_t)gf2_mulmod(gf2_table_entry(1u << i, t, POLY), skip, POLY, 32);
-            b[8][i] = (uint32_t)gf2_table_entry(1u << i, 0, POLY);
-        }
-    }
-};
-template <uint32_t POLY, int K>
-__device__ __forceinline__ uint32_t basis_w8(uint32_t e) {
-    constexpr BraidW8Basis<POLY> B{};
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v ^= ((e >> i) & 1u) ? B.b[K][i] : 0u;
-    return v;
-}
-// bt[i] = T'_t[1 << i] for a per-lane t < 8: one AND-OR per candidate through opaque masks (a select
-// chain over constants would become a per-lane load from a constant table, waited for behind the
-// payload loads already in flight)
-template <uint32_t POLY>
-__device__ __forceinline__ void basis_w8_lane(uint32_t t, uint32_t (&bt)[8]) {
-    constexpr BraidW8Basis<POLY> B{};
-    uint32_t m[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        m[k] = t == (uint32_t)k ? ~0u : 0u;
-        asm("" : "+v"(m[k]));
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v |= B.b[k][i] & m[k];
-        bt[i] = v;
-    }
-}
 // The eight slice-by-8 tables in 8 copies (64 KiB: one 256-byte row per entry e, table t at 32 t,
 // copies 0-3 then 4-7) from a 512-thread workgroup, as 4096 chunks of 16 bytes: chunk k = tid + 512 m
 // holds copies 4 (k & 1) .. + 3 of T'_t[e], t = (k & 15) >> 1, e = k >> 4 = (tid >> 4) + 32 m.
@@ -1899,18 +1822,6 @@ __device__ __forceinline__ void list_mask_edges(G &cur, uint32_t g, const LBuf &
     const uint64_t mh = (uint32_t)lane == lh ? ~0ull << (8 * sc.o) : ~0ull;
 #pragma unroll
     for (int R = 0; R < 8; ++R) cur.w[R] &= (uint32_t)R == jh ? mh : ~0ull;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t list_rsrc(uint64_t base, uint32_t nrec) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)rfl64(base), (short)0, (int)__builtin_amdgcn_readfirstlane(nrec),
-                                             0x00020000);
-}
-
-template <int R>
-__device__ __forceinline__ uint64_t bld_w8(__amdgpu_buffer_rsrc_t rs, uint32_t o0, uint32_t lim) {
-    const uint32_t o = __builtin_elementwise_min(o0 + (uint32_t)(R * kW8Row), lim);
-    const v2u v = __builtin_amdgcn_raw_buffer_load_b64(rs, o, 0, 2);  // aux 2: non-temporal
-    return ((uint64_t)v.y << 32) | v.x;
 }
 
 // stream_rows_w8 with the next group's rows read through a buffer resource

@@ -114,6 +114,8 @@ struct StreamState {
     Stage st;
     DevBuf xsums;   // split XXH3 long path: per-block accumulator sums
     DevBuf mp_out;  // multipart part results
+    DevBuf dual_tiles;  // fused CRC32 + CRC32C scan: a raw register pair per tile
+    DevBuf dual_tmp;    // its short-buffer route: split seeds and the two single scans' results
     // held by a multipart call on the stream from its list launch until its results are on the host:
     // two calls on one stream would otherwise queue launch A, launch B, then A's copy of B's results
     std::mutex mp_mu;
@@ -1629,6 +1631,112 @@ int single_impl(int alg, const void *input, size_t len, uint64_t seed, uint64_t 
     return 0;
 }
 
+// ---- fused CRC32 + CRC32C (aws_crt_amd_crc32_dual_strided)
+std::atomic<unsigned long long> g_dual_fused{0};
+
+// a per-stream device buffer of at least `need` bytes (under d->mu); never grown under capture
+int dual_reserve(Device *d, DevBuf &b, size_t need, hipStream_t s) {
+    if (b.bytes >= need) return 0;
+    if (capturing(s)) return fail(AWS_CRT_AMD_ERR_INVALID_ARG, "engine workspace must be warmed up before stream capture");
+    if (b.p) d->retired.push_back(b);  // queued launches may still use the old one
+    b = DevBuf{};
+    const size_t cap = std::max<size_t>(need, 4096);
+    HIP_TRY(hipMalloc(&b.p, cap));
+    b.bytes = cap;
+    return 0;
+}
+
+int dual_impl(Device *d, uint64_t base, size_t stride, size_t len, size_t count, const void *d_seeds, void *d_out, hipStream_t s) {
+    if (count > 0x7fffffffull) return fail(AWS_CRT_AMD_ERR_INVALID_ARG, "too many buffers");
+    const uint64_t ml = main_len(base, len);
+    if (ml < kDualMinTile) {
+        // no whole tile: the two single scans on split seeds, then the results paired (same stream)
+        uint32_t *tmp;
+        StreamState *ss;
+        {
+            std::lock_guard<std::mutex> g(d->mu);
+            ss = d->states.get(s);
+            int rc = dual_reserve(d, ss->dual_tmp, count * 16, s);
+            if (rc) return rc;
+            tmp = (uint32_t *)ss->dual_tmp.p;
+            if (d_seeds) {
+                const int e = amdcrc_launch_dual_split((const uint32_t *)d_seeds, tmp, tmp + count, count, s);
+                if (e) return fail(AWS_CRT_AMD_ERR_HIP, std::string("dual split launch: ") + hipGetErrorString((hipError_t)e));
+                t_used = ss;
+                fence_after(s);
+            }
+        }
+        int rc = strided_impl(d, ALG_CRC32, base, stride, len, count, d_seeds ? tmp : nullptr, 0, tmp + 2 * count, s);
+        if (!rc) rc = strided_impl(d, ALG_CRC32C, base, stride, len, count, d_seeds ? tmp + count : nullptr, 0, tmp + 3 * count, s);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> g(d->mu);
+        const int e = amdcrc_launch_dual_join(tmp + 2 * count, tmp + 3 * count, (uint32_t *)d_out, count, s);
+        if (e) return fail(AWS_CRT_AMD_ERR_HIP, std::string("dual join launch: ") + hipGetErrorString((hipError_t)e));
+        // (the state may have moved to the spares meanwhile; its buffer is fenced where it is)
+        t_used = ss;
+        fence_after(s);
+        return 0;
+    }
+    std::lock_guard<std::mutex> g(d->mu);
+    if (capturing(s) && (d->braid.find(ALG_CRC32) == d->braid.end() || d->braid.find(ALG_CRC32C) == d->braid.end()))
+        return fail(AWS_CRT_AMD_ERR_INVALID_ARG, "engine tables must be warmed up before stream capture");
+    const uint64_t *c32, *c32c;
+    int rc;
+    if ((rc = get_braid_consts(d, ALG_CRC32, &c32)) || (rc = get_braid_consts(d, ALG_CRC32C, &c32c))) return rc;
+    DualParams p{};
+    p.base = base;
+    p.stride = stride;
+    p.len = len;
+    p.count = count;
+    p.hoff = ((base + 15) & ~15ull) - base;
+    p.mainlen = ml;
+    // tiles of 1, 4, 16, 64 or 256 groups: the largest, no longer than the main region, that still gives
+    // every wave slot of the device a tile (fewer tile finishes per byte, fewer tiles for the finish pass)
+    const uint64_t slots = (uint64_t)d->cus * kDualWaves;
+    p.groups_per_tile = 1;
+    for (uint32_t g = 256; g > 1; g >>= 2)
+        if (g * kDualGroupBytes <= ml && count * ((ml + g * kDualGroupBytes - 1) / (g * kDualGroupBytes)) >= slots) {
+            p.groups_per_tile = g;
+            break;
+        }
+    const uint64_t tile = p.groups_per_tile * kDualGroupBytes;
+    p.tiles_per_buf = (ml + tile - 1) / tile;
+    p.ntiles = p.tiles_per_buf * count;
+    p.pad = (uint32_t)(p.tiles_per_buf * tile - ml);
+    const uint64_t blocks = std::min<uint64_t>((uint64_t)d->cus, (p.ntiles + kDualWaves - 1) / kDualWaves);
+    const uint64_t nw = blocks * kDualWaves;
+    p.split_q = p.ntiles / nw;
+    p.split_r = (uint32_t)(p.ntiles % nw);
+    p.d_k[0] = (const uint32_t *)c32 + kBraidK64Word;
+    p.d_k[1] = (const uint32_t *)c32c + kBraidK64Word;
+    p.xlev[0][0] = (uint32_t)gf2_xpow8n(tile, kPoly32, 32);
+    p.xlev[1][0] = (uint32_t)gf2_xpow8n(tile, kPoly32C, 32);
+    for (int l = 1; l < 32; ++l) {
+        p.xlev[0][l] = (uint32_t)gf2_mulmod(p.xlev[0][l - 1], p.xlev[0][l - 1], kPoly32, 32);
+        p.xlev[1][l] = (uint32_t)gf2_mulmod(p.xlev[1][l - 1], p.xlev[1][l - 1], kPoly32C, 32);
+    }
+    p.xmain[0] = (uint32_t)gf2_xpow8n(ml, kPoly32, 32);
+    p.xmain[1] = (uint32_t)gf2_xpow8n(ml, kPoly32C, 32);
+    p.d_seeds = (const uint32_t *)d_seeds;
+    p.d_out = (uint32_t *)d_out;
+    StreamState *ss = d->states.get(s);
+    if ((rc = dual_reserve(d, ss->dual_tiles, p.ntiles * 8, s))) return rc;
+    p.d_tiles = (uint32_t *)ss->dual_tiles.p;
+    const uint64_t T = p.tiles_per_buf;
+    int fth = 64;  // the finish pass's threads per buffer: a power of two, one tile each up to 1024
+    while (fth < 1024 && (uint64_t)fth < T) fth <<= 1;
+    t_used = ss;
+    const int e = amdcrc_launch_dual(&p, (int)blocks, fth, s, g_time_events);
+    g_time_events[0] = g_time_events[1] = nullptr;
+    if (e) {
+        t_used = nullptr;
+        return fail(AWS_CRT_AMD_ERR_HIP, std::string("dual scan launch: ") + hipGetErrorString((hipError_t)e));
+    }
+    g_dual_fused.fetch_add(1, std::memory_order_relaxed);
+    fence_after(s);
+    return 0;
+}
+
 }  // namespace
 
 // ================================================================== internal (abi_single.cpp)
@@ -1787,6 +1895,26 @@ AWS_CRT_AMD_API int aws_crt_amd_checksum_strided(int alg, const void *d_base, si
         if (count == 1) stride = len;
         return strided_impl(d, alg, (uint64_t)(uintptr_t)d_base, stride, len, count, d_seeds, 0, d_out, (hipStream_t)hip_stream);
     });
+}
+
+AWS_CRT_AMD_API int aws_crt_amd_crc32_dual_strided(const void *d_base, size_t stride, size_t len, size_t count,
+                                                   const void *d_seeds, void *d_out, void *hip_stream) {
+    return guarded(err_sink, [&]() -> int {
+        // the argument checks come before any device work (as aws_crt_amd_eventstream_crcs)
+        if (count == 0) return 0;
+        if (!d_out || (len && !d_base)) return fail(AWS_CRT_AMD_ERR_INVALID_ARG, "null buffer");
+        if (count == 1) stride = len;
+        if (count > 1 && (stride % 16) != 0)
+            return fail(AWS_CRT_AMD_ERR_INVALID_ARG, "strided batch needs stride % 16 == 0 (use the list API)");
+        Device *d;
+        int rc = get_device(&d);
+        if (rc) return rc;
+        return dual_impl(d, (uint64_t)(uintptr_t)d_base, stride, len, count, d_seeds, d_out, (hipStream_t)hip_stream);
+    });
+}
+
+AWS_CRT_AMD_API unsigned long long aws_crt_amd_crc32_dual_fused_launches(void) {
+    return g_dual_fused.load(std::memory_order_relaxed);
 }
 
 AWS_CRT_AMD_API int aws_crt_amd_checksum_batches(int alg, const struct aws_crt_amd_batch *batches, size_t nbatches,

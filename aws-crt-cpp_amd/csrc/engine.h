@@ -202,9 +202,39 @@ struct EventStreamParams {
 // x^(-8 t), t = 1..7 (image 60 + t - 1); 128 words each (nib_image)
 constexpr int kEsImages = 67;
 
+// Fused CRC32 + CRC32C scan (crc_dual_kernels.hip): count uniform buffers whose main
+// regions (the same length and alignment for all: stride % 16 == 0) are front-padded virtually to
+// tiles_per_buf tiles of groups_per_tile 4 KiB groups.  crc32_dual_stream_kernel stores each tile's raw
+// register pair to d_tiles; crc32_dual_finish_kernel joins them per buffer (xlev) with the seeds, head
+// and tail bytes.
+constexpr uint64_t kDualGroupBytes = 4096;            // 8 rows of 512 bytes: one ring slot of a wave
+constexpr uint64_t kDualMinTile = kDualGroupBytes;    // the smallest tile: main regions from here take the fused kernel
+constexpr int kDualBlock = 1024;                      // one workgroup per CU (144 KiB of LDS)
+constexpr int kDualWaves = kDualBlock / kWave;
+struct DualParams {
+    uint64_t base, stride, len, count;
+    uint64_t hoff;             // bytes from a buffer's start to its main region
+    uint64_t mainlen;
+    uint64_t tiles_per_buf, ntiles;
+    uint32_t groups_per_tile;  // 1, 4, 16, 64 or 256
+    uint32_t pad;              // virtual zero bytes in front of every main region (< tile)
+    uint64_t split_q;          // wave w scans tiles [w q + min(w, r), + q + (w < r))
+    uint32_t split_r;
+    uint32_t reserved0;
+    const uint32_t *d_k[2];    // K images of x^(-64 l), [j/4][lane][j%4] (get_braid_consts + kBraidK64Word)
+    uint32_t *d_tiles;         // per-stream workspace: (raw CRC32, raw CRC32C) per tile
+    const uint32_t *d_seeds;   // count pairs, or null
+    uint32_t *d_out;           // count pairs
+    uint32_t xlev[2][32];      // x^(8 * tile bytes * 2^l) per polynomial, l < 32 (the finish pass's shifts)
+    uint32_t xmain[2];         // x^(8 * mainlen) per polynomial
+};
+
 }  // namespace amdcrc
 
 extern "C" {
+int amdcrc_launch_dual(const amdcrc::DualParams *p, int nblocks, int finish_threads, void *stream, void *const *events);
+int amdcrc_launch_dual_split(const uint32_t *d_pairs, uint32_t *d_a, uint32_t *d_b, uint64_t n, void *stream);
+int amdcrc_launch_dual_join(const uint32_t *d_a, const uint32_t *d_b, uint32_t *d_pairs, uint64_t n, void *stream);
 int amdcrc_launch_eventstream(const amdcrc::EventStreamParams *p, void *stream, void *const *events);
 int amdcrc_launch_lanes(int alg, const amdcrc::LaneParams *p, void *stream, void *const *events);
 int amdcrc_launch_combine(int alg, const amdcrc::CombineParams *p, void *stream);

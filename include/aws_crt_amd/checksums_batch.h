@@ -129,6 +129,37 @@ AWS_CRT_AMD_API int aws_crt_amd_checksum_strided(
     void *hip_stream);
 
 /*
+ * CRC32 and CRC32C of the same bytes from one read of the data (BASELINE.json config 3's pair).
+ * Buffer i = [d_base + i*stride, + len), i < count.  d_seeds: device array of count pairs (previous
+ * CRCs, as previousCRC32 / previousCRC32C) or NULL for zero seeds; d_out: device array of count
+ * pairs.  stride % 16 == 0 or count == 1.  Asynchronous on hip_stream; errors as
+ * aws_crt_amd_checksum_strided (count 0 is a no-op; len 0 returns the seeds), the argument checks
+ * coming before any device work.
+ * Routing depends on (len, alignment, count) alone: buffers whose main region (the 16-byte-aligned
+ * interior) holds at least one tile -- the fused kernel's smallest tile, 4 KiB -- take the fused
+ * kernel, which loads every payload byte once and advances both polynomials from it (tiles of 4 KiB
+ * to 1 MiB: the largest that still gives every wave slot of the device one); shorter buffers run the
+ * two single scans and a small kernel pairs their results on the same stream.  Cross-tile state
+ * lives in the stream's state: calls on different streams may overlap, and a call can be captured on
+ * a stream after one warm-up call of the same shape (a workspace that would have to grow under
+ * capture is an error, never an allocation).
+ */
+struct aws_crt_amd_crc32_pair {
+    uint32_t crc32;
+    uint32_t crc32c;
+};
+AWS_CRT_AMD_API int aws_crt_amd_crc32_dual_strided(
+    const void *d_base,
+    size_t stride,
+    size_t len,
+    size_t count,
+    const void *d_seeds,
+    void *d_out,
+    void *hip_stream);
+/* launches of the fused kernel made by this process (like aws_crt_amd_fallback_count) */
+AWS_CRT_AMD_API unsigned long long aws_crt_amd_crc32_dual_fused_launches(void);
+
+/*
  * Several uniform batches of the same shape (stride, len, count), each with its own base, seeds and
  * results -- e.g. successive queued part batches.  CRC algorithms: up to 32 batches whose bases share
  * their alignment mod 16 go into ONE launch, so back-to-back batches do not each pay a launch's ramp
